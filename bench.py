@@ -1,8 +1,17 @@
 #!/usr/bin/env python3
 """bench.py — the driver's benchmark contract for the NewsRecommend hot path.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run does only what the headline figure needs: it builds the headline's
+index, warms up, times the K steps and prints the line (metric, value, unit,
+ms_per_step, the stage split and roofline the timed steps' own HIP events
+give).  --dump-outputs DIR writes what the last timed step returned (D.npy:
+the scores, float32; I.npy: the item ids, as float64) for comparing two builds
+output for output: the inputs are seeded, the same from run to run.  --full
+adds everything else described below: the recall / oracle checks, the
+cpu_baseline legs and the secondary records, one child process per record.
 
 Headline (BASELINE.json `metric`, configs[1]): exact flat retrieval, 1M x 128
 items, batches of nq = 4096 queries per GPU, k = 5, inner product.  One STEP =
@@ -110,7 +119,7 @@ def bench_flat(args, rank, world, dev):
     xq = clustered_corpus(nq, args.d, seed=4321, device=dev)
     index = ShardedIndexFlat(args.d, metric, device=dev)
     index.add_full(xb)
-    keep_full = rank == 0
+    keep_full = rank == 0 and args.full  # the host copy serves the recall check and the cpu_baseline only
     xb_host = xb.cpu().numpy() if keep_full else None
     del xb
     torch.cuda.empty_cache()
@@ -129,36 +138,45 @@ def bench_flat(args, rank, world, dev):
     barrier(world)
     el = max_over_ranks(time.perf_counter() - t0, world, dev)
     qps = nq * args.steps / el
+    if rank == 0 and args.dump_outputs:
+        _dump_outputs(args.dump_outputs, D, I)
+    fallback = index.local.fallback_counts.tolist()
+    out = {"value": qps, "unit": "queries/s", "ms_per_step": el / args.steps * 1e3,
+           "fallback_queries": fallback[0], "exact_scan_queries": fallback[1]}
 
     # per-stage device times (rank-local), averaged over the timed steps
-    if world > 1:  # one extra instrumented local search per step-count for the stage split
+    if world > 1 and args.full:  # one extra instrumented local search per step-count for the stage split
         for s in range(args.steps):
             index.local.search_device(xq, args.k, exact_scores=True, id_offset=index.offset, stage_events=evs[s])
         torch.cuda.synchronize()
-    st = np.array([e.elapsed_ms() for e in evs])
-    stage_ms = st.mean(0)
-    screen_ms = float(stage_ms[1])
-    flops = 2.0 * nq * nb_local * args.d
-    achieved = flops / (screen_ms * 1e-3) / 1e12
-    fallback = index.local.fallback_counts.tolist()
-
-    out = {
-        "value": qps, "unit": "queries/s", "ms_per_step": el / args.steps * 1e3,
-        "stages_ms": {"query_prepare+tau_prepass": float(stage_ms[0]), "screen": screen_ms,
-                      "merge_rescore": float(stage_ms[2]), "exact_fallback": float(stage_ms[3])},
-        "fallback_queries": fallback[0], "exact_scan_queries": fallback[1],
-        "roofline": {"bound": "mfma", "kernel": _screen_kernel_name(nq, nb_local, args.d, args.k, metric),
-                     "achieved": achieved, "peak": BF16_DENSE_TFLOPS, "unit": "TFLOP/s",
-                     "frac": achieved / BF16_DENSE_TFLOPS,
-                     "traffic": _pmc_traffic(f"nb={args.nb},d={args.d},nq={args.nq},k={args.k},metric={args.metric},"
-                                             f"gpus={world}"),
-                     "algorithmic": f"2*nq*nb_local*d = {flops:.4g} flop per launch"},
-    }
-    if rank == 0:
+    if world == 1 or args.full:
+        st = np.array([e.elapsed_ms() for e in evs])
+        stage_ms = st.mean(0)
+        screen_ms = float(stage_ms[1])
+        flops = 2.0 * nq * nb_local * args.d
+        achieved = flops / (screen_ms * 1e-3) / 1e12
+        out["stages_ms"] = {"query_prepare+tau_prepass": float(stage_ms[0]), "screen": screen_ms,
+                            "merge_rescore": float(stage_ms[2]), "exact_fallback": float(stage_ms[3])}
+        out["roofline"] = {"bound": "mfma", "kernel": _screen_kernel_name(nq, nb_local, args.d, args.k, metric),
+                           "achieved": achieved, "peak": BF16_DENSE_TFLOPS, "unit": "TFLOP/s",
+                           "frac": achieved / BF16_DENSE_TFLOPS,
+                           "traffic": _pmc_traffic(f"nb={args.nb},d={args.d},nq={args.nq},k={args.k},"
+                                                   f"metric={args.metric},gpus={world}"),
+                           "algorithmic": f"2*nq*nb_local*d = {flops:.4g} flop per launch"}
+    if rank == 0 and args.full:
         out["recall_at_5"], out["exact_match"] = _recall(args, xq, xb_host, D, I, metric)
         if world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = _cpu_flat(args, xq, xb_host, metric)
     return out
+
+
+def _dump_outputs(path, D, I):
+    """What the last timed step returned to its caller, as <path>/D.npy (the
+    top-k scores, float32) and <path>/I.npy (the item ids; int64 on the device,
+    written as float64, exact below 2^53)."""
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "D.npy"), D.cpu().numpy().astype(np.float32, copy=False))
+    np.save(os.path.join(path, "I.npy"), I.cpu().numpy().astype(np.float64))
 
 
 def _recall(args, xq, xb_host, D, I, metric):
@@ -1082,7 +1100,13 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--workload", choices=["flat", "din", "ivf", "e2e", "flow", "embed", "all"], default="all")
+    ap.add_argument("--full", action="store_true",
+                    help="also the recall / oracle checks, the cpu_baseline legs and the secondary records "
+                         "(default: the headline's timed steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the headline's last timed step returned to DIR/D.npy and DIR/I.npy")
+    ap.add_argument("--workload", choices=["flat", "din", "ivf", "e2e", "flow", "embed", "all"], default=None,
+                    help="with --full: the records to run (default all); a plain run is the headline, flat")
     ap.add_argument("--nb", type=int, default=1_000_000)
     ap.add_argument("--d", type=int, default=128)
     ap.add_argument("--nq", type=int, default=4096)
@@ -1112,6 +1136,14 @@ def main():
     ap.add_argument("--record", default=None, help=argparse.SUPPRESS)  # internal: the child's record
     ap.add_argument("--record-out", default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not args.full:  # a plain run: the headline record alone, in this process
+        if args.workload not in (None, "flat"):
+            ap.error(f"--workload {args.workload} needs --full (a plain run times the headline, flat, only)")
+        args.workload, args.no_isolate = "flat", True
+    elif args.workload is None:
+        args.workload = "all"
     if args.record:
         return child_main(args)
     if not args.no_isolate:

@@ -12,6 +12,7 @@ embedding_generate.py:20-22) -> we chdir into a temp dir holding synthetic
 `news/*.npy` dict-pickles that THIS script writes.
 
 Usage:  python tests/golden/make_golden.py
+        python tests/golden/make_golden.py embedding_train_run TAG   # this host's run of the triplet training only
 """
 from __future__ import annotations
 
@@ -409,12 +410,18 @@ def embedding_fixture(name, seed, n_articles=48):
                             emb=emb, table_loadable=np.bool_(table_loadable), **_sd(m))
 
 
-def embedding_train_fixture(name, seed, n_articles=120, n_train=16, n_test=9, max_clicks=8):
+def embedding_train_fixture(name, seed, n_articles=120, n_train=16, n_test=9, max_clicks=8, run_tag=None):
     """The reference's triplet training main() (embedding_generate.py:67-107),
     run as written (3 epochs, batch 64, shuffled loaders, dropout 0.13, Adam
     with weight decay, best-eval-loss checkpoint) on a small synthetic world.
     Every TripletMarginLoss value main() computes is recorded by handing the
-    module a loss subclass that logs (value, batch rows, train/eval)."""
+    module a loss subclass that logs (value, batch rows, train/eval).
+
+    The run repeats bit for bit on one host, but its fp32 CPU arithmetic
+    differs between CPU models from the first batch on (the same inputs give
+    losses a few 1e-6 apart, and Adam carries that into the weights).  With
+    `run_tag` only this host's run (losses + best checkpoint) is written, to
+    {name}_run_{run_tag}.npz next to the full fixture, whose inputs it shares."""
     with tempfile.TemporaryDirectory() as wd:
         rng = np.random.default_rng(seed)
         aids = rng.choice(np.arange(10, 10 * n_articles + 10), size=n_articles, replace=False)
@@ -453,6 +460,13 @@ def embedding_train_fixture(name, seed, n_articles=120, n_train=16, n_test=9, ma
             best = torch.load(os.path.join("news", "best_eg_model.pth"), weights_only=True)  # written by main() above
         finally:
             os.chdir(cwd)
+        run = dict(loss_values=np.array([v for v, _, _ in log], np.float64),
+                   loss_rows=np.array([b for _, b, _ in log], np.int64),
+                   loss_train=np.array([g for _, _, g in log], np.bool_),
+                   **{f"best::{k}": v.numpy() for k, v in best.items()})
+        if run_tag is not None:
+            np.savez_compressed(os.path.join(OUT, f"{name}_run_{run_tag}.npz"), **run)
+            return
         random.seed(seed)  # the triplets main() built (the datasets are its first `random` consumers)
         tr = np.asarray(ref.ArticleTripletDataset(True).triplets, np.int64)
         te = np.asarray(ref.ArticleTripletDataset(False).triplets, np.int64)
@@ -464,17 +478,16 @@ def embedding_train_fixture(name, seed, n_articles=120, n_train=16, n_test=9, ma
             test_users=np.array(list(tec.keys()), np.int64),
             test_click_len=np.array([len(v) for v in tec.values()], np.int64),
             test_clicks=np.concatenate([np.asarray(v, np.int64) for v in tec.values()]),
-            train_triplets=tr, test_triplets=te,
-            loss_values=np.array([v for v, _, _ in log], np.float64),
-            loss_rows=np.array([b for _, b, _ in log], np.int64),
-            loss_train=np.array([g for _, _, g in log], np.bool_),
-            **{f"best::{k}": v.numpy() for k, v in best.items()})
+            train_triplets=tr, test_triplets=te, **run)
 
 
 def main():
     torch.set_num_threads(4)
     if sys.argv[1:] == ["embedding_train"]:  # regenerate only the triplet-training fixture
         embedding_train_fixture("embedding_train", seed=18)
+        return
+    if sys.argv[1:2] == ["embedding_train_run"]:  # record this host's run of the same fixture: ... embedding_train_run TAG
+        embedding_train_fixture("embedding_train", seed=18, run_tag=sys.argv[2])
         return
     if sys.argv[1:] == ["din_rerank_cluster"]:  # regenerate only the whole-cluster re-rank fixture
         din_rerank_cluster_fixture("din_rerank_cluster", seed=19)

@@ -37,6 +37,17 @@ def test_cpu_rerank_user_is_the_reference_forward_in_any_chunking():
             assert torch.allclose(got, ref, atol=1e-5, rtol=1e-5), float((got - ref).abs().max())
 
 
+def test_plain_run_refuses_what_moved_behind_full(monkeypatch, capsys):
+    """A plain run is the headline alone: a secondary record asked for without
+    --full is an argument error (exit 2), not a silent headline run."""
+    for argv in (["--workload", "ivf"], ["--workload", "all"], ["--steps", "0"]):
+        monkeypatch.setattr("sys.argv", ["bench.py", "--gpus", "1", *argv])
+        with pytest.raises(SystemExit) as e:
+            bench.main()
+        assert e.value.code == 2, argv
+    assert "needs --full" in capsys.readouterr().err
+
+
 def test_cpu_e2e_and_flow_legs_report_the_contract_fields():
     torch.manual_seed(1)
     n, d, U, L = 3000, 64, 24, 10

@@ -165,10 +165,20 @@ def test_fit_triplet_matches_reference_main(tmp_path):
     typed click logs under the same `random` seed, then fit_triplet on the CPU
     under the same torch seed: the same batches, dropout masks and Adam
     steps, so every epoch's train/eval loss and the best-eval-loss checkpoint
-    match the reference's."""
+    match the reference's.
+
+    The reference's run is bit-reproducible on one host but not between CPU
+    models (fp32 CPU kernels are chosen per CPU: its first batch's loss
+    already differs by a few 1e-6, and Adam carries that into the weights,
+    up to 4e-4), so the fixture holds the reference's run as recorded on more
+    than one host (embedding_train.npz and embedding_train_run_*.npz, same
+    inputs, make_golden.py) and this host's run has to match one of them, each
+    to the same tolerances."""
     from newsrecommend_amd.embedding import ArticleEmbeddingModel, ArticleTripletDataset, fit_triplet
 
     z = np.load(os.path.join(GOLDEN, "embedding_train.npz"))
+    runs = [z] + [np.load(os.path.join(GOLDEN, f)) for f in sorted(os.listdir(GOLDEN))
+                  if f.startswith("embedding_train_run_") and f.endswith(".npz")]
     seed = int(z["seed"])
     tr_log, te_log = _fixture_logs(z)
     rng = random.Random(seed)
@@ -185,11 +195,24 @@ def test_fit_triplet_matches_reference_main(tmp_path):
         hist, best = fit_triplet(m, tr, te, z["aids"], torch.from_numpy(z["feats"]), save_path=path)
     finally:
         torch.set_num_threads(nt)
-    np.testing.assert_allclose(np.array(hist), np.array(_epoch_losses(z)), rtol=1e-6, atol=0)
     saved = torch.load(path, weights_only=True)
     for k, v in best.items():
-        np.testing.assert_allclose(v.numpy(), z[f"best::{k}"], rtol=0, atol=1e-6, err_msg=k)
         np.testing.assert_array_equal(saved[k].numpy(), v.numpy())
+
+    def matches(run):
+        np.testing.assert_allclose(np.array(hist), np.array(_epoch_losses(run)), rtol=1e-6, atol=0)
+        for k, v in best.items():
+            np.testing.assert_allclose(v.numpy(), run[f"best::{k}"], rtol=0, atol=1e-6, err_msg=k)
+
+    errors = []
+    for run in runs:
+        try:
+            matches(run)
+            break
+        except AssertionError as e:
+            errors.append(str(e))
+    else:
+        raise AssertionError(f"no recorded run of the reference matches ({len(runs)} recorded):\n" + "\n".join(errors))
 
 
 @pytest.mark.gpu

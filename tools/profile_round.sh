@@ -1,7 +1,8 @@
 #!/bin/bash
 # Kernel-trace stats + separate FETCH_SIZE / WRITE_SIZE passes of the bench
 # (MI355X_MICROARCH.md §HBM: the two TCC counters do not fit one pass).
-# usage (on the GPU box, from the repo root): bash tools/profile_round.sh TAG [bench args...]
+# usage (on a machine with the GPU, from the repo root): bash tools/profile_round.sh TAG [bench args...]
+# all records in one profiled process: bench args "--full --no-isolate"; no args: the headline's plain run
 set -eo pipefail
 TAG=$1; shift
 OUT=$GRAFT_REPO_ROOT/gpurun_out/prof_$TAG
