@@ -1608,6 +1608,7 @@ struct FlatPlan {
   int small_P;
   int64_t small_ld, small_chunk;
   int dp, qt, M, waves, wq, nqt, nch, U, KP;
+  int pre_waves, nqt_pre;     // threshold pre-pass: waves per workgroup, query tiles (its own tile size)
   int R, nch_pre, tstride;  // threshold pre-pass: bound rank, chunks, tile stride
   int fb_slots, fb_cap;     // tiled fallback: slots with candidate storage, candidates per slot
   int64_t nq_pad, chunk, chunk_pre;
@@ -1645,12 +1646,22 @@ static int host_pow2ceil(int n) {
 //                         pass and the IVF collect (test_knn_gpu.py
 //                         ::test_screen_main_pass_forms, test_ivf_gpu.py
 //                         ::test_ivf_collect_forms)
+//   NRK_SCREEN_WAVES=4|8  the flat inner-product main pass at padded dim 128,
+//                         k <= 8: 4 forces the 256-query (4-wave) workgroups
+//                         where the plan would run 512-query (8-wave) ones, 8
+//                         forces those below the plan's query count
+//                         (test_knn_screen_w8.py; tools/bench_screen.py A/B)
 static int test_hook(const char* name, int dflt) {
   const char* v = getenv(name);
   return v && *v ? atoi(v) : dflt;
 }
 
-static FlatPlan make_plan(int64_t nq, int64_t nb, int d, int k) {
+// query count from which the DP = 128 inner-product main pass runs 512-query workgroups
+// (screen ms, 4 vs 8 waves in one process at 1M x 128, k = 5: 512 queries 0.122 vs
+// 0.122, 1024 0.226 vs 0.231, 2048 0.413 vs 0.413, 4096 0.783 vs 0.774)
+constexpr int64_t W8_MIN_NQ = 4096;
+
+static FlatPlan make_plan(int64_t nq, int64_t nb, int d, int k, bool l2) {
   FlatPlan p;
   memset(&p, 0, sizeof(p));
   p.dp = padded_dim(d);
@@ -1684,6 +1695,14 @@ static FlatPlan make_plan(int64_t nq, int64_t nb, int d, int k) {
   // screen 17.4 -> 15.0 ms) and, at k = 200, a chunk far larger than L2
   // re-read by half as many query tiles
   if (p.dp == 256 && (p.M == 4 || p.M == 16)) p.waves = 8;
+  // DP = 128, M = 4, inner product (the 16x16x32 form): 8-wave workgroups of 512
+  // queries, one per CU, from W8_MIN_NQ queries on (below 512 half a workgroup
+  // scans zero rows).  One staged tile serves twice the queries: half the
+  // LDS-DMA pieces per MFMA.  The pre-pass keeps its 4-wave kernel.
+  if (p.dp == 128 && p.M == 4 && !l2 && test_hook("NRK_SCREEN16", 1)) {
+    const int force = test_hook("NRK_SCREEN_WAVES", 0);
+    if (force == 8 || (force != 4 && nq >= W8_MIN_NQ)) p.waves = 8;
+  }
   // R: tau bounds the R-th best screened score from the pre-pass's lane maxima
   // (every stride-th tile), so it sits near global rank ~stride * R; the main
   // pass then admits ~stride * R items per query (list insertions, the VALU
@@ -1701,6 +1720,8 @@ static FlatPlan make_plan(int64_t nq, int64_t nb, int d, int k) {
   p.wq = p.waves * 32 * p.qt;
   p.nqt = (int)cdiv(nq, p.wq);
   p.nq_pad = (int64_t)p.nqt * p.wq;
+  p.pre_waves = p.dp == 128 ? 4 : p.waves;
+  p.nqt_pre = (int)(p.nq_pad / (p.pre_waves * 32 * p.qt));
   // k > 24 (M = 16): twice the lane streams, so that dense neighbourhoods do
   // not overflow a lane's list (10M x 256, k = 200: 2 uncertified queries per
   // 4096 -> 0, and the 4.5 ms fp64 fallback scan with them)
@@ -1719,7 +1740,10 @@ static FlatPlan make_plan(int64_t nq, int64_t nb, int d, int k) {
       while (st < 64 && (int64_t)st * p.R < 4 * (int64_t)k) st *= 2;
     p.tstride = st;
   }
-  int target = p.M >= 16 ? 2048 : 1024;
+  // workgroups: four rounds of one per CU (two of the 4-wave form run on a CU
+  // at a time; the DP = 128 8-wave form, one per CU, takes two rounds, which
+  // keeps the chunk count and so the merge's union: 4096 queries -> 64 chunks)
+  int target = p.M >= 16 ? 2048 : (p.dp == 128 && p.waves == 8) ? 512 : 1024;
   int64_t nch = target / (p.nqt > 0 ? p.nqt : 1);
   // ... but at least enough chunks (2 lane streams each) that the ~stride * R
   // items above tau spread to <= M per stream: with many query tiles (a
@@ -1932,9 +1956,11 @@ extern "C" int nrk_padded_dim(int32_t d) { return padded_dim(d); }
 // other form runs; a test hook).
 static screen_fn main_pass(const FlatPlan& p, bool l2, bool* s16) {
   *s16 = false;
-  screen_fn fn = p.waves == 8 ? pick_screen_dp256_w8(p.M, l2, 0) : pick_screen(p.dp, p.qt, p.M, l2, 0);
+  // (DP = 128 with 8 waves is planned only for the 16x16x32 form)
+  screen_fn fn = p.waves == 8 ? (p.dp == 256 ? pick_screen_dp256_w8(p.M, l2, 0) : nullptr)
+                              : pick_screen(p.dp, p.qt, p.M, l2, 0);
   if (!l2 && test_hook("NRK_SCREEN16", 1)) {
-    screen_fn f16 = p.waves == 8 ? (p.dp == 256 ? pick_screen16_dp256_w8(p.M) : nullptr)
+    screen_fn f16 = p.waves == 8 ? (p.dp == 256 ? pick_screen16_dp256_w8(p.M) : pick_screen16_dp128_w8(p.qt, p.M))
                                  : (p.dp == 128 ? pick_screen16_dp128(p.qt, p.M) : nullptr);
     if (f16) {
       fn = f16;
@@ -1947,8 +1973,8 @@ static screen_fn main_pass(const FlatPlan& p, bool l2, bool* s16) {
 extern "C" int nrk_knn_flat_main_pass(int64_t nq, int64_t nb, int32_t d, int32_t k, int32_t metric, char* name,
                                       size_t len) {
   NRK_CHECK_ARG(name && len > 0 && nq >= 0 && nb >= 0 && d > 0 && k > 0, "knn_flat_main_pass: bad arguments");
-  const FlatPlan p = make_plan(nq, nb, d, k);
   const bool l2 = metric == NRK_METRIC_L2;
+  const FlatPlan p = make_plan(nq, nb, d, k, l2);
   if (p.small) snprintf(name, len, "small_exact (fp64 tile GEMM, no screen)");
   else if (p.exact_only) snprintf(name, len, "exact_topk_kernel (fp64 brute force, no screen)");
   else {
@@ -1976,7 +2002,10 @@ extern "C" int nrk_flat_prepare(const float* xb, int64_t nb, int32_t d, uint16_t
 
 extern "C" int nrk_knn_flat_workspace(int64_t nq, int64_t nb, int32_t d, int32_t k, size_t* ws_bytes) {
   NRK_CHECK_ARG(ws_bytes && nq >= 0 && nb >= 0 && d > 0 && k > 0, "knn_flat_workspace: bad arguments");
-  *ws_bytes = make_plan(nq, nb, d, k).total;
+  // (no metric here: the larger of the two plans, which differ where the inner
+  // product runs 8-wave workgroups)
+  const size_t ip = make_plan(nq, nb, d, k, false).total, l2 = make_plan(nq, nb, d, k, true).total;
+  *ws_bytes = ip > l2 ? ip : l2;
   return NRK_OK;
 }
 
@@ -2000,7 +2029,7 @@ extern "C" int nrk_knn_flat(const float* xq, int64_t nq, const float* xb, const 
                 (long long)nq, (long long)nb, d, k);
   NRK_CHECK_ARG(metric == NRK_METRIC_INNER_PRODUCT || metric == NRK_METRIC_L2, "knn_flat: bad metric %d", metric);
   hipStream_t st = (hipStream_t)stream;
-  FlatPlan p = make_plan(nq, nb, d, k);
+  FlatPlan p = make_plan(nq, nb, d, k, metric == NRK_METRIC_L2);
   // L2: rescore at least the top 128 screened candidates.  The certificate
   // needs the k-th exact score to clear theta (>= the best candidate NOT
   // rescored) by the screening-error bound, which for squared L2 on clustered
@@ -2073,10 +2102,11 @@ extern "C" int nrk_knn_flat(const float* xq, int64_t nq, const float* xb, const 
                      p.dp, qh, qmeta, fbc, n_fallback);
   NRK_CHECK_LAUNCH("query_prepare_kernel");
   if (p.tau) {
-    screen_fn pf = p.waves == 8 ? pick_screen_dp256_w8(p.M, l2 != 0, 1) : pick_screen(p.dp, p.qt, p.M, l2 != 0, 1);
+    screen_fn pf =
+        p.pre_waves == 8 ? pick_screen_dp256_w8(p.M, l2 != 0, 1) : pick_screen(p.dp, p.qt, p.M, l2 != 0, 1);
     if (!pf) return fail(NRK_EUNSUPPORTED, "knn_flat: no pre-pass kernel for dp=%d", p.dp);
-    hipLaunchKernelGGL(pf, dim3(p.nqt * p.nch_pre), dim3(p.waves * 64), 0, st, qh, xb_bf16, xb_meta, nq, nb,
-                       p.chunk_pre, p.nch_pre, p.nqt, p.tstride, nullptr, nullptr, pre, nullptr, IvfScreen{});
+    hipLaunchKernelGGL(pf, dim3(p.nqt_pre * p.nch_pre), dim3(p.pre_waves * 64), 0, st, qh, xb_bf16, xb_meta, nq, nb,
+                       p.chunk_pre, p.nch_pre, p.nqt_pre, p.tstride, nullptr, nullptr, pre, nullptr, IvfScreen{});
     NRK_CHECK_LAUNCH("screen_kernel (pre-pass)");
     const int nv = 2 * p.nch_pre;
     auto tsel = nv <= 64 ? tau_select_kernel<1> : nv <= 256 ? tau_select_kernel<4> : tau_select_kernel<16>;

@@ -80,18 +80,19 @@ __global__ __launch_bounds__(WAVES * 64, 2) void screen16_kernel(
   const int q16 = lane & 15, g = lane >> 4;
   const int ntiles = (int)cdiv(iend - ibeg, TI);
 
+  // the lane's query row of half-tile t (< nq_pad: rows past nq are zero)
+  auto qrow = [&](int t) { return (int64_t)qt * WQ + (int64_t)w * QT * 32 + 16 * t + q16; };
   bf16x8 qf[NQ2][KS2];
-  int64_t qidx[NQ2];
-  float tau[NQ2];
+  // admission threshold max(ls[t][M], tau): starts at tau, raised by every insertion
+  float thr[NQ2];
   float ls[NQ2][M + 1];
   int li[NQ2][M + 1];
 #pragma unroll
   for (int t = 0; t < NQ2; ++t) {
-    qidx[t] = (int64_t)qt * WQ + (int64_t)w * QT * 32 + 16 * t + q16;  // < nq_pad (zero rows)
-    const bf16x8* src = reinterpret_cast<const bf16x8*>(qh + qidx[t] * DP + 8 * g);
+    const bf16x8* src = reinterpret_cast<const bf16x8*>(qh + qrow(t) * DP + 8 * g);
 #pragma unroll
     for (int s = 0; s < KS2; ++s) qf[t][s] = src[4 * s];
-    tau[t] = (tau_q && qidx[t] < nq) ? tau_q[qidx[t]] : -INFINITY;
+    thr[t] = (tau_q && qrow(t) < nq) ? tau_q[qrow(t)] : -INFINITY;
 #pragma unroll
     for (int j = 0; j <= M; ++j) {
       ls[t][j] = -INFINITY;
@@ -101,18 +102,16 @@ __global__ __launch_bounds__(WAVES * 64, 2) void screen16_kernel(
 
   const int64_t cnt = iend - ibeg > 0 ? iend - ibeg : 0;
   const BufRsrc xrs = make_rsrc(xbh + ibeg * DP, (int)(cnt * DP * 2));
-  int voff[GPT];
-#pragma unroll
-  for (int u = 0; u < GPT; ++u) {
-    const int p = u * NT + tid;
-    const int row = p / CPR, pc = p % CPR;
-    voff[u] = row * DP * 2 + 16 * (pc ^ swz<CPR>(row));
-  }
+  // a thread's rows of a tile are NT / CPR apart, a multiple of the swizzle's
+  // 16-row period: one vector offset, the rest in the scalar offset
+  static_assert((NT / CPR) % 16 == 0, "staging rows per pass: a multiple of the swizzle period");
+  const int voff = (tid / CPR) * DP * 2 + 16 * ((tid % CPR) ^ swz<CPR>(tid / CPR));
   auto issue_tile = [&](int it, auto buf_c) {
     constexpr int buf = decltype(buf_c)::value;
     const int soff = it * TI * DP * 2;
 #pragma unroll
-    for (int u = 0; u < GPT; ++u) buffer_load_lds16(xrs, lds + buf * BUF + (u * NT + w * 64) * 8, voff[u], soff);
+    for (int u = 0; u < GPT; ++u)
+      buffer_load_lds16(xrs, lds + buf * BUF + (u * NT + w * 64) * 8, voff, soff + u * (NT / CPR) * DP * 2);
   };
   // A fragment: row `row` of a tile image, K step s (lane group g reads chunk 4 s + g)
   auto afrag = [&](const uint16_t* tl, int row, int s) {
@@ -143,24 +142,28 @@ __global__ __launch_bounds__(WAVES * 64, 2) void screen16_kernel(
       m[t] = fmax_ieee(m2[t][0], m2[t][1]);
     }
   };
+  // Hit path: one compare per half-tile against thr on the straight line; the
+  // ballot masks of those compares pick the half-tiles to visit.
   auto drain = [&](f32x4 (&pa)[NQ2][2], int64_t pbase, const float (&m2)[NQ2][2], const float (&m)[NQ2])
       __attribute__((always_inline)) {
-    bool hit = false;
-#pragma unroll
-    for (int t = 0; t < NQ2; ++t) hit |= m[t] > fmaxf(ls[t][M], tau[t]);
-    if (!__any(hit)) return;
+    unsigned long long hit[NQ2], any = 0;
 #pragma unroll
     for (int t = 0; t < NQ2; ++t) {
-      if (__any(m[t] > fmaxf(ls[t][M], tau[t]))) {
+      hit[t] = __ballot(m[t] > thr[t]);
+      any |= hit[t];
+    }
+    if (!any) return;
 #pragma unroll
-        for (int ih = 0; ih < 2; ++ih) {
-          if (__any(m2[t][ih] > fmaxf(ls[t][M], tau[t]))) {
+    for (int t = 0; t < NQ2; ++t) {
+      if (!hit[t]) continue;
 #pragma unroll
-            for (int v = 0; v < 4; ++v) {
-              const float thr = fmaxf(ls[t][M], tau[t]);
-              if (pa[t][ih][v] > thr)
-                list_insert<M + 1>(ls[t], li[t], pa[t][ih][v], (int)(pbase + 16 * ih + 4 * g + v));
-            }
+      for (int ih = 0; ih < 2; ++ih) {
+        if (!__ballot(m2[t][ih] > thr[t])) continue;
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+          if (pa[t][ih][v] > thr[t]) {
+            list_insert<M + 1>(ls[t], li[t], pa[t][ih][v], (int)(pbase + 16 * ih + 4 * g + v));
+            thr[t] = fmax_ieee(thr[t], ls[t][M]);
           }
         }
       }
@@ -269,7 +272,7 @@ __global__ __launch_bounds__(WAVES * 64, 2) void screen16_kernel(
     if (g < 2) {
 #pragma unroll
       for (int j = 0; j <= M; ++j) list_insert_tie<M + 1>(ls[t], li[t], ps[j], pi[j]);
-      const int64_t qi = qidx[t];
+      const int64_t qi = qrow(t);
       if (qi < nq) {
         const int64_t base = (qi * nch + c) * 2 + g;
 #pragma unroll
@@ -641,6 +644,7 @@ screen_fn pick_collect16_dp128(bool l2);
 
 // the 16x16x32 main pass for (DP, qt, M), or nullptr (no such form: use screen.h's)
 screen_fn pick_screen16_dp128(int qt, int M);
+screen_fn pick_screen16_dp128_w8(int qt, int M);
 screen_fn pick_screen16_dp256_w8(int M);
 
 }  // namespace nrk
