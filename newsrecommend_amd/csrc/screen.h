@@ -1,8 +1,9 @@
 // screen.h — the bf16 MFMA screening kernel (K-GEMM-TOPK / K-IVF-SCAN) and
 // its per-padded-dimension dispatch.  The template is instantiated in one
 // translation unit per padded dimension (screen_dp{32,64,128,256}.hip) so the
-// build compiles the ~200 instantiations in parallel; knn_flat.hip only calls
-// pick_screen().
+// build compiles the 62 instantiations (16 per padded dimension below 256, 14
+// at 256; screen16.h adds 6) in parallel; knn_flat.hip and ivf_search.hip only
+// call pick_screen().
 #pragma once
 
 #include <math.h>
@@ -129,16 +130,16 @@ __device__ __forceinline__ void list_insert(float (&ls)[N], int (&li)[N], float 
 //   pre-pass bound removes the warm-up insertions that otherwise dominate.
 //   The merge's certificate includes tau[q] in theta.
 //
-// MODE 2 (IVF list scan): the block's work item comes from a device table —
-//   (list l, tile of the queries probing l, chunk of l).  qh holds the probing
-//   queries gathered list-major (segments padded to WQ rows); slot_pair maps a
-//   gathered row back to its (query, probe) pair, whose candidates land at
-//   [(pair * cmax + chunk) * 2 + half].
-// MODE 3 (IVF collect): MODE 2's work items, no lane lists: every item whose
-//   screened score reaches the query's threshold is appended to the query's
-//   candidate buffer (rare: the threshold sits just below the k-th best).
-// MODE 4 (IVF lane maxima): MODE 2's work items, MODE 1's epilogue (each lane
-//   writes the maximum screened score of its stream).
+// The IVF modes (3 and 4; there is no mode 2) take the block's work items from
+//   a device table: (list l, tile of the queries probing l, chunk of l).  qh
+//   holds the probing queries gathered list-major (segments padded to WQ rows);
+//   slot_pair maps a gathered row back to its (query, probe) pair.
+// MODE 3 (IVF collect): no lane lists: every item whose screened score reaches
+//   the query's threshold is appended to the query's candidate buffer (rare:
+//   the threshold sits just below the k-th best).
+// MODE 4 (IVF lane maxima): MODE 1's epilogue plus the position (each lane
+//   writes the maximum screened score of its stream and where it was, at
+//   [(pair * cmax + chunk) * 2 + half]).
 struct IvfScreen {
   const int* work_off;     // [nlist + 1] prefix of work items per list
   const int64_t* list_off; // [nlist + 1] list ranges in the list-major corpus
@@ -195,7 +196,8 @@ __global__ __launch_bounds__(WAVES * 64, (MODE == 3 && WAVES == 8) ? 1 : 2) void
   constexpr int KS = DP / 16;
   constexpr int WQ = WAVES * 32 * QT;
   constexpr int BUF = TI * DP + 2 * TI;  // uint16 per buffer: rows + TI float norms
-  static_assert(!DEFER || MODE <= 1 || MODE == 3 || MODE == 4, "deferred epilogue: flat modes, IVF collect / lane maxima");
+  static_assert(MODE == 0 || MODE == 1 || MODE == 3 || MODE == 4, "modes: main pass, pre-pass, IVF collect, IVF lane maxima");
+  static_assert(!DEFER || MODE <= 1, "deferred epilogue: flat modes only");
   __shared__ __attribute__((aligned(16))) uint16_t lds[2 * BUF];
   __shared__ std::conditional_t<MODE == 3, CollectLds<WQ>, NoLds> cl;
 
@@ -464,47 +466,8 @@ __global__ __launch_bounds__(WAVES * 64, (MODE == 3 && WAVES == 8) ? 1 : 2) void
         m[t] = fmax_ieee(fmax_ieee(m4[t][0], m4[t][1]), fmax_ieee(m4[t][2], m4[t][3]));
       }
     };
-    // rare part: lane-list insertions (MODE 0) or the lane maximum (MODE 1)
+    // rare part: lane-list insertions (MODE 0); MODE 1 only keeps the lane maximum
     auto drain = [&](f32x16 (&pa)[QT], int64_t pbase, const float (&m4)[QT][4], const float (&m)[QT]) __attribute__((always_inline)) {
-      if constexpr (MODE == 3) {  // IVF collect: append every score at or above the query's threshold
-  #pragma unroll
-        for (int t = 0; t < QT; ++t) {
-          if (__any(m[t] >= cthr[t])) {
-  #pragma unroll
-            for (int g = 0; g < 16; ++g) {
-              if (pa[t][g] >= cthr[t]) {
-                const int pos = (int)(pbase + (g & 3) + 8 * (g >> 2) + 4 * h);
-                const int e = atomicAdd(&cl.n, 1);
-                if (e < CollectLds<WQ>::CAP) {
-                  const int row = (w * QT + t) * 32 + r;
-                  const int rank = atomicAdd(&cl.qcnt[row], 1);
-                  cl.ent[e] = make_int2(row | (rank << 10), pos);
-                } else if (guard_ok((uint64_t)cq[t] < (uint64_t)nq, iv.err, GUARD_COLLECT_QUERY) &&
-                           __builtin_nontemporal_load(&iv.cand_cnt[cq[t]]) <= iv.cap) {
-                  const int slot = atomicAdd(&iv.cand_cnt[cq[t]], 1);
-                  if (slot < iv.cap) iv.cand_pos[(int64_t)cq[t] * iv.cap + slot] = pos;
-                }
-              }
-            }
-          }
-        }
-        return;
-      }
-      if constexpr (MODE == 4) {  // IVF lane maximum and its position
-  #pragma unroll
-        for (int t = 0; t < QT; ++t) {
-          if (__any(m[t] > ls[t][0])) {
-  #pragma unroll
-            for (int g = 0; g < 16; ++g) {
-              if (pa[t][g] > ls[t][0]) {
-                ls[t][0] = pa[t][g];
-                li[t][0] = (int)(pbase + (g & 3) + 8 * (g >> 2) + 4 * h);
-              }
-            }
-          }
-        }
-        return;
-      }
       if constexpr (MODE == 1) {
   #pragma unroll
         for (int t = 0; t < QT; ++t) ls[t][0] = fmax_ieee(ls[t][0], m[t]);
@@ -668,9 +631,7 @@ __global__ __launch_bounds__(WAVES * 64, (MODE == 3 && WAVES == 8) ? 1 : 2) void
     for (int t = 0; t < QT; ++t) {
       const int64_t qi = qidx[t];
       int64_t base = -1;
-      if constexpr (MODE == 3) {
-        continue;  // collect mode writes its candidates as it goes
-      } else if constexpr (MODE == 2 || MODE == 4) {
+      if constexpr (MODE == 4) {
         const int pair = iv.slot_pair[seg0 + qi];
         if (pair >= 0) base = ((int64_t)pair * iv.cmax + c) * 2 + h;
       } else if (qi < nq) {
@@ -698,7 +659,7 @@ __global__ __launch_bounds__(WAVES * 64, (MODE == 3 && WAVES == 8) ? 1 : 2) void
 typedef void (*screen_fn)(const uint16_t*, const uint16_t*, const float*, int64_t, int64_t, int64_t, int, int, int,
                           float*, int*, float*, const float*, IvfScreen);
 
-// The one kernel variant per (DP, QT, M, L2, MODE).  Flat modes (main pass and
+// The one 4-wave kernel variant per (DP, QT, M, L2, MODE).  Flat modes (main pass and
 // pre-pass) defer each sub-tile's epilogue into the next MFMA chain, except
 // where the second accumulator set and the fragment prefetch would spill (DP =
 // 256, L2 with two query tiles, the DP = 128 two-tile pre-pass); the IP main
@@ -714,8 +675,12 @@ constexpr screen_fn screen_variant() {
     return screen_kernel<DP, QT, M, 4, L2, MODE, (MODE >= 2)>;
 }
 
-// mode: 0 main pass, 1 threshold pre-pass, 2 IVF list scan, 3 IVF collect, 4 IVF lane maxima.
-// DP = 256 always runs one query tile per wave.
+// mode: 0 main pass, 1 threshold pre-pass, 3 IVF collect, 4 IVF lane maxima.
+// Only the forms a plan can launch are built (DESIGN.md "K-GEMM-TOPK" has the
+// table); any other (qt, M, mode) returns nullptr, which the callers report as
+// NRK_EUNSUPPORTED.  DP = 256 always runs one query tile per wave, and its
+// 4-wave main pass exists for M = 8 only (M = 4 and 16 run 8 waves:
+// pick_screen_dp256_w8).
 template <int DP, bool L2>
 screen_fn screen_for(int qt, int M, int mode) {
   constexpr int Q2 = DP == 256 ? 1 : 2;
@@ -723,18 +688,13 @@ screen_fn screen_for(int qt, int M, int mode) {
   switch (mode) {
     case 1: return two ? screen_variant<DP, Q2, 1, L2, 1>() : screen_variant<DP, 1, 1, L2, 1>();
     case 3: return two ? screen_variant<DP, Q2, 1, L2, 3>() : screen_variant<DP, 1, 1, L2, 3>();
-    case 4: return two ? screen_variant<DP, Q2, 1, L2, 4>() : screen_variant<DP, 1, 1, L2, 4>();
+    case 4: return two ? nullptr : screen_variant<DP, 1, 1, L2, 4>();  // phase A: one query tile
     case 0:
-    case 2: {
-      if (mode == 0) {
-        if (M == 4) return two ? screen_variant<DP, Q2, 4, L2, 0>() : screen_variant<DP, 1, 4, L2, 0>();
-        if (M == 8) return screen_variant<DP, 1, 8, L2, 0>();
-        return screen_variant<DP, 1, 16, L2, 0>();
+      if (M == 8 && !two) return screen_variant<DP, 1, 8, L2, 0>();
+      if constexpr (DP < 256) {
+        if (M == 4 && two) return screen_variant<DP, 2, 4, L2, 0>();  // k <= 8: always two tiles
+        if (M == 16 && !two) return screen_variant<DP, 1, 16, L2, 0>();
       }
-      if (M == 4) return two ? screen_variant<DP, Q2, 4, L2, 2>() : screen_variant<DP, 1, 4, L2, 2>();
-      if (M == 8) return screen_variant<DP, 1, 8, L2, 2>();
-      return screen_variant<DP, 1, 16, L2, 2>();
-    }
   }
   return nullptr;
 }
